@@ -23,6 +23,16 @@ the fused HIP kernels; ``--no-graph`` disables HIP-graph capture of the step.
 (ImageNet shape 3×224×224, 1000 classes, batch 256) and ``vit_b16`` (3×224×224,
 1000 classes, batch 128) — all bf16 autocast, DDP over RCCL for N>1, SGD(momentum)
 for the ResNets and AdamW for ViT, synthetic HBM-resident data (stored bf16).
+
+``--dump-outputs DIR`` writes what the last timed step handed back to its caller, as
+``DIR/<name>.npy`` (float32): the step's ``logits`` and ``loss`` and every parameter after that
+step's update (``param.<name>``).  Data, weights and shuffling are seeded, so two runs with the same
+arguments see identical inputs.  At most 64 MB are written: when the arrays hold more, the large
+ones are reduced to a fixed, seeded sample of their elements.
+
+A plain run sets up, warms up, times the steps and prints the result line.  ``--full`` adds the
+end-of-run check that is not needed for the headline figure: the float64 weight checksums and their
+cross-rank comparison (``dp.weight_checksum``, ``dp.replicas_identical``).
 """
 
 from __future__ import annotations
@@ -103,10 +113,61 @@ def _weight_checksum(net) -> list:
     return [s0.item(), s1.item()]
 
 
-def _dp_record(mod, net, ctx, comm) -> dict:
+DUMP_BUDGET_BYTES = 60 * 2**20  # --dump-outputs writes at most 64 MB; headers and small arrays fit in the rest
+DUMP_KEEP_WHOLE = 1 << 16      # arrays up to this many elements are never sampled
+
+
+def _make_dump_timer(base):
+    """A StepTimer that, once the timed window has closed, keeps copies of what the last timed step
+    returned (the model's output batch and the loss the Loss capsule published).  Copies, because a
+    captured step's outputs live in the graph memory pool, which is released with the run."""
+
+    class DumpTimer(base):
+        logits = None
+        loss = None
+
+        def launch(self, attrs=None):
+            base.launch(self, attrs)
+            if self.steps is not None and self._i == self.warmup + self.steps and attrs is not None:
+                batch = attrs.get("batch")
+                if isinstance(batch, (list, tuple)) and len(batch) > 2:
+                    self.logits = batch[2].detach().float().clone()
+                looper = attrs.get("looper")
+                if looper is not None and looper.state.loss is not None:
+                    self.loss = float(looper.state.loss)
+
+    return DumpTimer
+
+
+def _dump_outputs(path: str, timer, net) -> None:
+    import numpy as np
+
+    arrays = {}
+    if timer.logits is not None:
+        arrays["logits"] = timer.logits.cpu().numpy()
+    if timer.loss is not None:
+        arrays["loss"] = np.asarray([timer.loss], dtype=np.float32)
+    for name, p in net.named_parameters():
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        small = sum(a.nbytes for a in arrays.values() if a.size <= DUMP_KEEP_WHOLE)
+        frac = (DUMP_BUDGET_BYTES - small) / (total - small)
+        rng = np.random.default_rng(1234)
+        for name in sorted(arrays):
+            a = arrays[name]
+            if a.size > DUMP_KEEP_WHOLE:
+                idx = np.sort(rng.choice(a.size, size=max(1, int(a.size * frac)), replace=False))
+                arrays[name] = a.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _dp_record(mod, net, ctx, comm, full: bool) -> dict:
     """What ran: the data-parallel transport and capture mode, bucket sizes, how many ranks the
-    communicator spans, the capture counters, and whether the replicas ended bit-identical
-    (cross-rank weight checksums, compared on every rank)."""
+    communicator spans and the capture counters; with ``full`` also whether the replicas ended
+    bit-identical (cross-rank weight checksums, compared on every rank)."""
     from rocket_amd.parallel.ddp import DataParallel
 
     rep = getattr(mod, "_module", None)
@@ -128,10 +189,11 @@ def _dp_record(mod, net, ctx, comm) -> dict:
     if g is not None:
         rec["graph"] = {"captures": g.captures, "replays": g.replays, "parts": g.parts,
                         "launch_lists": g.launch_lists}
-    sums = _weight_checksum(net)
-    parts = comm.all_gather_object(sums) if ctx.world_size > 1 else [sums]
-    rec["weight_checksum"] = sums
-    rec["replicas_identical"] = all(p == parts[0] for p in parts)
+    if full:
+        sums = _weight_checksum(net)
+        parts = comm.all_gather_object(sums) if ctx.world_size > 1 else [sums]
+        rec["weight_checksum"] = sums
+        rec["replicas_identical"] = all(p == parts[0] for p in parts)
     return rec
 
 
@@ -149,6 +211,10 @@ def main() -> int:
     ap.add_argument("--graph", action="store_true", help="force HIP-graph capture for the non-LeNet models")
     ap.add_argument("--mp", default="bf16")
     ap.add_argument("--cpu", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the end-of-run replica check (weight checksums compared across ranks)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return _spawn(args.gpus)
@@ -213,7 +279,8 @@ def main() -> int:
     # step-time p50 from timing events every `stride` steps (an event per ~80 us LeNet step would
     # itself cost ~5 us of queue time); the headline number is the barrier/sync-bracketed wall time
     stride = max(10, args.steps // 50) if args.model == "lenet" else 1
-    timer = StepTimer(warmup=args.warmup, steps=args.steps, stride=stride)
+    timer_cls = _make_dump_timer(StepTimer) if args.dump_outputs else StepTimer
+    timer = timer_cls(warmup=args.warmup, steps=args.steps, stride=stride)
     launcher = rocket.Launcher(
         [
             rocket.Looper(
@@ -264,7 +331,9 @@ def main() -> int:
 
     elapsed = timer.elapsed
     summ = timer.summary()
-    dp = _dp_record(mod, net, ctx, comm)
+    dp = _dp_record(mod, net, ctx, comm, args.full)
+    if args.dump_outputs and ctx.rank == 0:
+        _dump_outputs(args.dump_outputs, timer, net)
     stats = torch.tensor([elapsed, summ.get("step_ms_p50", 0.0)], dtype=torch.float64)
     if world > 1:
         parts = comm.all_gather_object(stats.tolist())

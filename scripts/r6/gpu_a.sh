@@ -16,7 +16,7 @@ w2() {  # tag, extra env
   for r in 0 1; do
     env "$@" MASTER_ADDR=127.0.0.1 MASTER_PORT=$port WORLD_SIZE=2 LOCAL_WORLD_SIZE=2 RANK=$r LOCAL_RANK=$r \
       ROCKET_DIST_BACKEND=gloo ROCKET_P2P=force timeout -k 10 240 rocprofv3 --kernel-trace --stats \
-      -d $O/$tag/r$r -o run -- python bench.py --gpus 2 --steps 300 --warmup 20 > $O/${tag}_r$r.json 2> $O/${tag}_r$r.err &
+      -d $O/$tag/r$r -o run -- python bench.py --gpus 2 --steps 300 --warmup 20 --full > $O/${tag}_r$r.json 2> $O/${tag}_r$r.err &
   done
   wait -n || return 1
   wait -n || return 1
