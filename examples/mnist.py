@@ -87,6 +87,7 @@ def main() -> int:
     ap.add_argument("--test-size", type=int, default=10000, help="synthetic evaluation samples")
     ap.add_argument("--save-every", type=int, default=50, help="Checkpointer cadence (iterations)")
     ap.add_argument("--capture", type=int, default=None, help="HIP-graph capture of the train step (default: on GPUs)")
+    ap.add_argument("--clip", type=float, default=None, help="clip gradients to this global L2 norm (default: off)")
     args = ap.parse_args()
 
     from rocket_amd.runtime import comm
@@ -117,7 +118,8 @@ def main() -> int:
             rocket.Looper(
                 [
                     rocket.Dataset(train, batch_size=args.batch, shuffle=True),
-                    rocket.Module(net, [rocket.Loss(CrossEntropy()), rocket.Optimizer(opt), rocket.Scheduler(sched)],
+                    rocket.Module(net, [rocket.Loss(CrossEntropy()), rocket.Optimizer(opt, max_grad_norm=args.clip),
+                                        rocket.Scheduler(sched)],
                                   capture=dev.type == "cuda" if args.capture is None else bool(args.capture)),
                     rocket.Tracker(backend="jsonl"),
                     rocket.Checkpointer(save_every=args.save_every),

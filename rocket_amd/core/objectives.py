@@ -12,13 +12,17 @@ Parity:
   (Q14: same values, no host synchronisation).
 * ``Optimizer`` — reference ``rocket/core/optimizer.py``: ``step()`` +
   ``zero_grad()`` each grad-enabled micro-step (the engine wrapper gates them on
-  sync), per-group lr posted to tracker/looper on sync steps.
+  sync), per-group lr posted to tracker/looper on sync steps.  An extension over
+  the reference: ``max_grad_norm`` (keyword only) clips the gradients to a global
+  L2 norm before every update and posts ``{tag}.grad_norm`` /
+  ``looper.state.grad_norm`` on sync steps.
 * ``Scheduler`` — reference ``rocket/core/scheduler.py``: ``step()`` each
   grad-enabled micro-step (wrapper steps ×W on sync steps).
 """
 
 from __future__ import annotations
 
+import math
 import os
 import weakref
 
@@ -186,11 +190,30 @@ def _is_fused_scaler(scaler) -> bool:
 
 
 class Optimizer(Capsule):
-    def __init__(self, optimizer: torch.optim.Optimizer, tag: str = "opt", priority: int = 1000) -> None:
+    """Steps and zeroes ``optimizer`` on gradient-sync micro-steps and posts its learning rates.
+
+    ``max_grad_norm`` (keyword only, an extension over the reference): clip the gradients to this
+    global L2 norm before every update (``torch.nn.utils.clip_grad_norm_`` semantics; ``None`` = no
+    clipping) and post ``{tag}.grad_norm`` / ``looper.state.grad_norm`` on sync steps.  The fused
+    optimizers clip on the device inside their update (``set_grad_clip``: one extra launch, no host
+    read, graph-capturable); any other optimizer goes through ``engine.clip_grad_norm_`` on
+    gradient-sync steps.  With clipping on, a captured step keeps the update as a launch of its
+    own: the global norm needs every final gradient before any element is updated, so the gradient
+    producers' update epilogues are not armed (the fused LeNet step is then 4 launches, not 2)."""
+
+    def __init__(self, optimizer: torch.optim.Optimizer, tag: str = "opt", priority: int = 1000, *,
+                 max_grad_norm: float | None = None) -> None:
         super().__init__(statefull=False, priority=priority)
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
+                raise ValueError(f"max_grad_norm must be a finite positive number, got {max_grad_norm}")
         self._optimizer = optimizer
         self._tag = tag
         self._iter_idx = 0
+        self._max_grad_norm = max_grad_norm
+        self._norm_posted = 0  # fused clip: the optimizer's clipped launches reported so far
+        self._norm_lap = []    # weak references to this ring lap's posted LazyScalars
 
     def setup(self, attrs: Attributes | None = None) -> None:
         Capsule.setup(self, attrs=attrs)
@@ -199,8 +222,38 @@ class Optimizer(Capsule):
         if len(found) > 1:
             raise RuntimeError(f"{self.__class__.__name__}: same optimizer has been registered twice.")
         self._optimizer = found[0] if found else engine.prepare_optimizer(self._optimizer)
+        if self._max_grad_norm is not None:
+            inner = self._fused_clip_target()
+            if inner is not None:
+                inner.set_grad_clip(self._max_grad_norm)
+                self._norm_posted = inner.norm_launches
+            else:
+                self._optimizer.clip_max_norm = self._max_grad_norm
+
+    def _fused_clip_target(self):
+        """The wrapped optimizer when it clips inside its own update (the fused optimizers)."""
+        inner = getattr(self._optimizer, "optimizer", self._optimizer)
+        return inner if hasattr(inner, "set_grad_clip") else None
+
+    def _clipping(self):
+        """The fused optimizer whose launches currently include the norm pass, or None."""
+        if self._max_grad_norm is None:
+            return None
+        inner = self._fused_clip_target()
+        return inner if inner is not None and inner.max_grad_norm is not None else None
+
+    def _norm_lap_guard(self, inner) -> None:
+        """Before a clipped launch: if it starts a new lap of the optimizer's norm ring, resolve what
+        the last lap posted (a consumer may keep a reported norm across a whole lap) before the
+        slots are rewritten — Loss.graph_prepare's rule."""
+        if self._norm_lap and inner.norm_launches % inner.GRAD_NORM_RING == 0:
+            materialize([r() for r in self._norm_lap if r() is not None])
+            self._norm_lap = []
 
     def step(self) -> None:
+        inner = self._clipping()
+        if inner is not None and self._accelerator.sync_gradients:
+            self._norm_lap_guard(inner)
         if hasattr(self._optimizer, "step_and_zero_grad"):
             self._optimizer.step_and_zero_grad()
         else:
@@ -211,13 +264,36 @@ class Optimizer(Capsule):
         if not self._accelerator.sync_gradients:
             return
         data = {f"{self._tag}.lr.{i}": g.get("lr") for i, g in enumerate(self._optimizer.param_groups)}
+        lrs = list(data.values())
+        norm = self._take_norm() if self._max_grad_norm is not None else None
+        if norm is not None:
+            data[f"{self._tag}.grad_norm"] = norm
         if attrs is not None:
             tracker, looper = attrs.get("tracker"), attrs.get("looper")
             if tracker is not None:
                 tracker.scalars.append(Attributes(step=self._iter_idx, data=data))
             if looper is not None:
-                looper["state"]["lr"] = list(data.values())
+                looper["state"]["lr"] = lrs
+                if norm is not None:
+                    looper["state"]["grad_norm"] = norm
         self._iter_idx += 1
+
+    def _take_norm(self):
+        """This sync step's global gradient norm as a device-backed value (no host read), or None
+        when no clip ran (no gradients, or grad disabled)."""
+        inner = self._clipping()
+        if inner is not None:
+            n = inner.norm_launches
+            if n == self._norm_posted:
+                return None
+            self._norm_posted = n
+            value = LazyScalar(inner.grad_norm_slot(n - 1))  # the ring slot that launch wrote
+            self._norm_lap.append(weakref.ref(value))
+            return value
+        norm, self._optimizer.last_grad_norm = getattr(self._optimizer, "last_grad_norm", None), None
+        if norm is None:
+            return None
+        return LazyScalar(norm) if isinstance(norm, torch.Tensor) else norm
 
     def launch(self, attrs: Attributes | None = None) -> None:
         if torch.is_grad_enabled():
@@ -244,12 +320,18 @@ class Optimizer(Capsule):
         else:
             inner.refresh_hyper()  # pointers are frozen into the graph; only lr & co. can change
         engine = self._accelerator
+        clip = self._clipping() is not None
+        if clip and engine.sync_gradients:
+            self._norm_lap_guard(inner)
         if hasattr(inner, "epilogue_armed"):
             # exact only when the backward's gradients ARE the step's final gradients: one replica,
             # a gradient-sync step and no AMP scaler.  A fused gradient producer (the LeNet weight-
             # gradient launch) then applies the update itself; see _FusedBase.epilogue.
+            # Global-norm clipping rules both update epilogues out: the norm needs every final
+            # gradient before any element is updated, so the step keeps its separate launches
+            # (norm, then update).  The AMP check fold only flags values: it may stay.
             inner.epilogue_armed = (engine.sync_gradients and engine.num_processes == 1 and engine.scaler is None
-                                    and _OPT_EPILOGUE)
+                                    and _OPT_EPILOGUE and not clip)
             # under the device fp16 scaler the same producer can instead flag non-finite gradients
             # itself (the step's separate check launch is then skipped; see _FusedBase.amp_checked):
             # exact when its gradients are final and local ones are all there is (one replica)
@@ -259,7 +341,7 @@ class Optimizer(Capsule):
             # back instead (DataParallel._reduce_with_update); exact under the same conditions with
             # the REDUCED gradients as the final ones
             inner.reduce_epilogue_armed = (engine.sync_gradients and engine.num_processes > 1 and engine.scaler is None
-                                           and _OPT_EPILOGUE)
+                                           and _OPT_EPILOGUE and not clip)
             if (inner.epilogue_armed or inner.amp_fold_armed or inner.reduce_epilogue_armed) and \
                     not getattr(self, "_epi_tagged", False):
                 for g in inner.param_groups:
@@ -276,6 +358,9 @@ class Optimizer(Capsule):
             if getattr(inner, "epilogue_done", False):
                 inner.epilogue_done = False  # the gradient producer applied this step's update
                 return
+            # (clipping under data parallelism needs nothing more: this runs after the reduction
+            # join, the reduced gradients are identical on every rank, so each rank's norm launch
+            # computes the same norm and coefficient bit for bit — no collective)
             scaler = self._accelerator.scaler
             if scaler is not None:
                 scaler.step_device(inner, zero_grads=True)  # flag check + scaled update, in-graph
@@ -290,6 +375,8 @@ class Optimizer(Capsule):
             inner.amp_fold_armed = False
         if getattr(inner, "reduce_epilogue_armed", False):
             inner.reduce_epilogue_armed = False
+        if self._accelerator.sync_gradients and self._clipping() is not None:
+            inner.norm_launches += 1  # the replayed step ran the norm launch (the capture did not count it)
         scaler = self._accelerator.scaler
         if scaler is not None and self._accelerator.sync_gradients:
             # the skipped-step flag of the replayed update: copied behind it, read only if asked

@@ -86,12 +86,13 @@ template <typename G, bool ZG, int J>
 __global__ void __launch_bounds__(kThreads) adam_mt_kernel(const TensorRec* __restrict__ tensors,
                                                           const int2* __restrict__ blocks,
                                                           const AdamHyper* __restrict__ hyper, float* step,
-                                                          float* amp, unsigned* counter) {
+                                                          float* amp, const float* clip, unsigned* counter) {
   // block record + chunk index + step counter loads all in flight at once (the tensor table holds
   // one record per BLOCK: no dependent table walk before the data loads)
   const int2 bt = blocks[blockIdx.x];
   const TensorRec tr = tensors[blockIdx.x];
   const bool skip = amp != nullptr && amp[kAmpFound] != 0.f;
+  const float coef = clip ? clip[kClipCoef] : 1.f;  // global-norm clipping (grad_norm_mt_kernel ran before)
   const float cur = read_step(step);
   const float t = cur + 1.f;
   if (!skip) {
@@ -101,7 +102,7 @@ __global__ void __launch_bounds__(kThreads) adam_mt_kernel(const TensorRec* __re
     float* __restrict__ m = (float*)tr.s0;
     float* __restrict__ v = (float*)tr.s1;
     const AdamStep k = adam_step(h, t);
-    const float gs = amp ? amp[kAmpInv] : 1.f;
+    const float gs = (amp ? amp[kAmpInv] : 1.f) * coef;
     constexpr int CH = J * 4 * kThreads;
     const int64_t start = (int64_t)bt.y * CH;
     const int64_t end = min(start + (int64_t)CH, tr.n);
@@ -179,10 +180,11 @@ template <typename G, bool ZG, int J>
 __global__ void __launch_bounds__(kThreads) sgd_mt_kernel(const TensorRec* __restrict__ tensors,
                                                          const int2* __restrict__ blocks,
                                                          const SgdHyper* __restrict__ hyper, float* step,
-                                                         float* amp, unsigned* counter) {
+                                                         float* amp, const float* clip, unsigned* counter) {
   const int2 bt = blocks[blockIdx.x];
   const TensorRec tr = tensors[blockIdx.x];
   const bool skip = amp != nullptr && amp[kAmpFound] != 0.f;
+  const float coef = clip ? clip[kClipCoef] : 1.f;
   const float cur = read_step(step);
   if (!skip) {
     const SgdHyper h = hyper[tr.group];
@@ -190,7 +192,7 @@ __global__ void __launch_bounds__(kThreads) sgd_mt_kernel(const TensorRec* __res
     G* __restrict__ g = (G*)tr.g;
     float* __restrict__ buf = (float*)tr.s0;
     const bool first = cur == 0.f;  // momentum buffer initialised with the first gradient (torch semantics)
-    const float gs = amp ? amp[kAmpInv] : 1.f;
+    const float gs = (amp ? amp[kAmpInv] : 1.f) * coef;
     const float sgn = h.maximize != 0.f ? -1.f : 1.f;
     constexpr int CH = J * 4 * kThreads;
     const int64_t start = (int64_t)bt.y * CH;
@@ -286,19 +288,138 @@ RK_API int rk_amp_check(int gdtype, const void* tensors, const void* blocks, int
   return (int)hipGetLastError();
 }
 
+// Global L2 norm of every gradient of the tables and the clipping coefficient that follows from it
+// (torch.nn.utils.clip_grad_norm_, error_if_nonfinite=False), one launch, no host read: each block
+// sums g*g over its chunk into partials[block]; the last block to arrive adds the partials in a
+// fixed order (no float atomics: the norm is bitwise reproducible) and writes the clip block
+// (ClipSlot layout): norm = amp[kAmpInv] * sqrt(sum) — the norm of the UNSCALED gradients under
+// fp16 loss scaling — and coef = min(1, max_norm / (norm + 1e-6)), which the update launch that
+// follows multiplies into every gradient.  The norm also goes to ring[*slot % ring_n] (reported to
+// the host lazily, as Loss does) and the cursor advances.
+//
+// The last-block election is two-level: tickets on ONE address serialise (~12 ns each measured: the
+// 21 k blocks of a ViT-B/16 set would wait ~250 us on them, 4x the time of streaming the
+// gradients), so each group of kNormGroup consecutive blocks takes tickets on a counter of its own
+// (one 128-byte line each) and only the last block of a group takes one on tickets[0].  The
+// hand-off rule is rk_common.h's last_block_arrived at both levels: partials stored with st_sc1 and
+// drained before the block's first ticket, tickets are agent-scope atomics, and a group's last
+// block takes its second ticket only after the first has returned, so every partial is complete
+// before the ticket that elects the last block.  Every counter is left at zero (graph replays).
+constexpr int kNormGroup = 64;
+constexpr int kNormTicketStride = 32;  // uint32 between the groups' counters
+
+__device__ __forceinline__ bool last_block_arrived_grouped(unsigned* tickets, int* smem_flag) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned nb = gridDim.x, grp = blockIdx.x / kNormGroup;
+    const unsigned ngrp = (nb + kNormGroup - 1) / kNormGroup;
+    const unsigned gsz = min((unsigned)kNormGroup, nb - grp * kNormGroup);
+    unsigned* gc = tickets + (size_t)(1 + grp) * kNormTicketStride;
+    int last = 0;
+    if (__hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsz - 1) {
+      __hip_atomic_store(gc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the whole group has been here
+      last = __hip_atomic_fetch_add(tickets, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ngrp - 1;
+    }
+    *smem_flag = last;
+  }
+  __syncthreads();
+  return *smem_flag != 0;
+}
+
+template <typename G, int J>
+__global__ void __launch_bounds__(kThreads) grad_norm_mt_kernel(const TensorRec* __restrict__ tensors,
+                                                               const int2* __restrict__ blocks, const float* amp,
+                                                               float* partials, float* clip, float* ring,
+                                                               long long* slot, int ring_n, unsigned* counter) {
+  __shared__ float s_red[kThreads / 64];
+  __shared__ int s_last;
+  const int2 bt = blocks[blockIdx.x];
+  const TensorRec tr = tensors[blockIdx.x];
+  constexpr int CH = J * 4 * kThreads;
+  const int64_t start = (int64_t)bt.y * CH;
+  const int64_t end = min(start + (int64_t)CH, tr.n);
+  const G* __restrict__ g = (const G*)tr.g;
+  float acc = 0.f;
+  if (sizeof(G) == 4 && (tr.g & 15) == 0 && end - start == CH) {
+    // full chunk: all J float4 loads of the thread in flight before the first multiply
+    float4 gg[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) gg[j] = *(const float4*)((const float*)g + start + 4 * (threadIdx.x + j * kThreads));
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      acc = __builtin_fmaf(gg[j].x, gg[j].x, acc);
+      acc = __builtin_fmaf(gg[j].y, gg[j].y, acc);
+      acc = __builtin_fmaf(gg[j].z, gg[j].z, acc);
+      acc = __builtin_fmaf(gg[j].w, gg[j].w, acc);
+    }
+  } else {
+    for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
+      const float v = gload<G>(g, i);
+      acc = __builtin_fmaf(v, v, acc);
+    }
+  }
+  const float part = block_sum(acc, s_red);
+  if (threadIdx.x == 0) st_sc1(partials + blockIdx.x, part);
+  if (!last_block_arrived_grouped(counter, &s_last)) return;
+  float a = 0.f;
+  for (unsigned i = threadIdx.x; i < gridDim.x; i += kThreads) a += ld_sc1(partials + i);
+  const float sum = block_sum(a, s_red);
+  if (threadIdx.x == 0) {
+    const float norm = (amp ? amp[kAmpInv] : 1.f) * sqrtf(sum);
+    const float c = clip[kClipMax] / (norm + 1e-6f);
+    clip[kClipNorm] = norm;
+    clip[kClipCoef] = c > 1.f ? 1.f : c;  // a NaN norm gives a NaN coefficient, as torch's clamp does
+    if (ring) {
+      const long long n = *slot;
+      ring[n % ring_n] = norm;
+      *slot = n + 1;
+    }
+  }
+  reset_counter(counter);
+}
+
+// partials: float[nblocks]; clip: float[kClipSlots]; ring/slot: nullptr or the reporting ring of
+// ring_n floats and its int64 cursor; counter: rk_grad_norm_tickets(nblocks) zeroed uint32 of this
+// launch's own (the kernel leaves them zeroed).
+RK_API int rk_grad_norm_tickets(int nblocks) {
+  return (1 + (nblocks + kNormGroup - 1) / kNormGroup) * kNormTicketStride;
+}
+RK_API int rk_grad_norm_mt(int gdtype, const void* tensors, const void* blocks, int nblocks, const float* amp,
+                           float* partials, float* clip, float* ring, void* slot, int ring_n, unsigned* counter,
+                           int chunk, hipStream_t s) {
+  if (nblocks <= 0) return 0;
+  if (chunk != kChunk && chunk != kChunk / 4) return (int)hipErrorInvalidValue;
+  if (!partials || !clip || !counter || (ring && (!slot || ring_n <= 0))) return (int)hipErrorInvalidValue;
+  const TensorRec* t = (const TensorRec*)tensors;
+  const int2* b = (const int2*)blocks;
+  long long* sl = (long long*)slot;
+#define RK_NORM_LAUNCH(G, J) \
+  grad_norm_mt_kernel<G, J><<<nblocks, kThreads, 0, s>>>(t, b, amp, partials, clip, ring, sl, ring_n, counter)
+  if (gdtype == BF16)
+    chunk == kChunk ? RK_NORM_LAUNCH(uint16_t, 4) : RK_NORM_LAUNCH(uint16_t, 1);
+  else
+    chunk == kChunk ? RK_NORM_LAUNCH(float, 4) : RK_NORM_LAUNCH(float, 1);
+#undef RK_NORM_LAUNCH
+  return (int)hipGetLastError();
+}
+
 // kind: 0 = Adam/AdamW, 1 = SGD.  gdtype: grads dtype (0 f32, 1 bf16).  chunk: 1024 or 4096.
 // amp: nullptr, or the device loss-scaling state (AmpSlot layout): gradients are unscaled by
 // amp[kAmpInv] inside the update, a set found flag makes the step a no-op (step counter kept),
 // and the last block applies the scale update.
+// clip: nullptr, or the clip block rk_grad_norm_mt filled on the same stream: every gradient is
+// also multiplied by clip[kClipCoef].
 RK_API int rk_optim_mt(int kind, int gdtype, const void* tensors, const void* blocks, int nblocks, const void* hyper,
-                       float* step, float* amp, unsigned* counter, int zero_grads, int chunk, hipStream_t s) {
+                       float* step, float* amp, const float* clip, unsigned* counter, int zero_grads, int chunk,
+                       hipStream_t s) {
   if (nblocks <= 0) return 0;
   if (chunk != kChunk && chunk != kChunk / 4) return (int)hipErrorInvalidValue;
   const TensorRec* t = (const TensorRec*)tensors;
   const int2* b = (const int2*)blocks;
 #define RK_OPT_LAUNCH_J(KERNEL, G, H, J)                                                                              \
-  (zero_grads ? KERNEL<G, true, J><<<nblocks, kThreads, 0, s>>>(t, b, (const H*)hyper, step, amp, counter) \
-              : KERNEL<G, false, J><<<nblocks, kThreads, 0, s>>>(t, b, (const H*)hyper, step, amp, counter))
+  (zero_grads ? KERNEL<G, true, J><<<nblocks, kThreads, 0, s>>>(t, b, (const H*)hyper, step, amp, clip, counter) \
+              : KERNEL<G, false, J><<<nblocks, kThreads, 0, s>>>(t, b, (const H*)hyper, step, amp, clip, counter))
 #define RK_OPT_LAUNCH(KERNEL, G, H) \
   (chunk == kChunk ? RK_OPT_LAUNCH_J(KERNEL, G, H, 4) : RK_OPT_LAUNCH_J(KERNEL, G, H, 1))
   if (kind == 0) {

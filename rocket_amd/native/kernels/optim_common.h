@@ -62,6 +62,11 @@ enum AmpSlot { kAmpScale = 0, kAmpInv, kAmpFound, kAmpTracker, kAmpGrowth, kAmpB
                kAmpSeq, kAmpHost = 10, kAmpSlots = 12 };
 constexpr int kAmpRing = 64;
 
+// Global-norm gradient clipping (optim.hip grad_norm_mt_kernel -> the multi-tensor update):
+//   clip[0] max_norm (uploaded by the host; changing it invalidates no graph), clip[1] the last
+//   global L2 norm of the (unscaled) gradients, clip[2] coef = min(1, max_norm / (norm + 1e-6)).
+enum ClipSlot { kClipMax = 0, kClipNorm, kClipCoef, kClipSlots = 4 };
+
 // torch._amp_update_scale_, executed by the optimizer launch's last block
 __device__ __forceinline__ void amp_update(float* amp) {
   const float found = amp[kAmpFound];

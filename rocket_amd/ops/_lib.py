@@ -96,8 +96,11 @@ KERNEL_SIGS = {
     "rk_mlp3_wgrad_loss": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                    c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p]),
     "rk_lenet_train": (c_int, [c_void_p] * 18 + [c_int, c_void_p, c_void_p, c_void_p]),
-    "rk_optim_mt": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+    "rk_optim_mt": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_int, c_int, c_void_p]),
+    "rk_grad_norm_tickets": (c_int, [c_int]),
+    "rk_grad_norm_mt": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_int, c_void_p, c_int, c_void_p]),
     "rk_amp_check": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "rk_host_mapped_alloc": (c_void_p, [c_int64, c_void_p]),
     "rk_gap_fwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

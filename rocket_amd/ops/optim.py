@@ -18,6 +18,7 @@ from __future__ import annotations
 
 from typing import List, Optional
 
+import math
 import operator
 
 import torch
@@ -57,6 +58,18 @@ class _FusedBase(torch.optim.Optimizer):
         # data parallel over the P2P kernel: an identity AmpSlot block whose found flag a timed-out
         # reduction raises (parallel/p2p.py), read by unscaled launches so they skip that update
         self.guard: Optional[torch.Tensor] = None
+        # global-norm gradient clipping (set_grad_clip): not a param-group entry, so state_dict /
+        # optimizer.bin stay interchangeable with torch's
+        self.max_grad_norm: Optional[float] = None
+        self._clip = None          # device clip block (optim_common.h ClipSlot: max_norm, norm, coef)
+        self._clip_sent = None     # the max_norm the device holds
+        self._clip_host = None
+        self._partials = None      # one sum of squares per block of the tables
+        self._norm_tickets = None  # the norm launch's own zeroed ticket counters (rk_grad_norm_tickets)
+        self._norm_ring = None     # reported norms, one slot per clipped launch
+        self._norm_slot = None     # device write cursor into the ring
+        self._norm_views = None
+        self.norm_launches = 0     # clipped launches so far (host count of the device cursor)
 
     # ----------------------------------------------------------- host side
     def _active(self) -> List[tuple]:
@@ -117,8 +130,64 @@ class _FusedBase(torch.optim.Optimizer):
     #: the param-group entries _hyper_row reads (raw values: an unchanged step is one tuple compare)
     HYPER_KEYS: tuple = ()
 
+    #: slots of the reported-norm ring (see grad_norm_slot)
+    GRAD_NORM_RING = 1024
+
+    def set_grad_clip(self, max_norm: Optional[float]) -> None:
+        """Clip the gradients to a global L2 norm of ``max_norm`` inside every update (``None``: off).
+
+        ``torch.nn.utils.clip_grad_norm_(params, max_norm)`` semantics over this optimizer's active
+        parameters, with no host read: :meth:`launch` first enqueues one norm launch over the same
+        block tables, then the update multiplies every gradient by the coefficient it left on the
+        device.  Under a loss scaler the norm is that of the unscaled gradients.  Changing the
+        value re-uploads one float; switching clipping on or off invalidates captured graphs."""
+        if max_norm is not None:
+            max_norm = float(max_norm)
+            if not (math.isfinite(max_norm) and max_norm > 0.0):
+                raise ValueError(f"max_norm must be a finite positive number, got {max_norm}")
+        if (max_norm is None) != (self.max_grad_norm is None):
+            self.version += 1  # the step gains / loses a launch
+        self.max_grad_norm = max_norm
+
+    def _refresh_clip(self) -> None:
+        """Allocate the clipping state with the tables and upload ``max_norm`` if it changed."""
+        if self.max_grad_norm is None or self._device is None:
+            return
+        dev = self._device
+        if self._clip is None or self._clip.device != dev:
+            self._clip = torch.zeros(4, dtype=torch.float32, device=dev)  # optim_common.h kClipSlots
+            self._norm_ring = torch.zeros(self.GRAD_NORM_RING, dtype=torch.float32, device=dev)
+            self._norm_slot = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._norm_views = list(self._norm_ring.unbind(0))  # one 0-d view per slot, made once
+            self.norm_launches = 0
+            self._clip_sent = None
+            self._partials = None
+            self.version += 1
+        if self._partials is None or self._partials.numel() < self._nblocks:
+            self._partials = torch.empty(max(self._nblocks, 1), dtype=torch.float32, device=dev)
+            # tickets of the norm launch's last-block election: its own counters (never the update's
+            # optim_{id} one), zeroed once — the kernel leaves them at zero
+            self._norm_tickets = torch.zeros(int(_lib.kernels().rk_grad_norm_tickets(max(self._nblocks, 1))),
+                                             dtype=torch.int32, device=dev)
+            self.version += 1
+        if self._clip_sent != self.max_grad_norm:
+            host = torch.tensor([self.max_grad_norm], dtype=torch.float32).pin_memory()
+            self._clip[0:1].copy_(host, non_blocking=True)
+            self._clip_host = host  # keep the pinned source alive until the copy has run
+            self._clip_sent = self.max_grad_norm
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """0-dim device view of the global gradient norm the last clipped launch measured."""
+        return None if self._clip is None else self._clip[1]
+
+    def grad_norm_slot(self, n: int) -> torch.Tensor:
+        """0-dim device view of the ring slot that clipped launch number ``n`` (0-based) writes."""
+        return self._norm_views[n % len(self._norm_views)]
+
     def refresh_hyper(self) -> None:
         """Upload the per-group hyper-parameters if a scheduler/user changed them (cheap when unchanged)."""
+        self._refresh_clip()
         if self.HYPER_KEYS:
             get = self._hyper_get
             if get is None:
@@ -155,6 +224,7 @@ class _FusedBase(torch.optim.Optimizer):
         b_host = torch.tensor(blocks, dtype=torch.int32).pin_memory()
         self._tables = (t_host.to(device, non_blocking=True), b_host.to(device, non_blocking=True))
         self._nblocks = len(blocks) // 2
+        self._partials = None  # sized with the block table (_refresh_clip)
         for _, p in active:  # the kernel now keeps these parameters' bf16 shadows current
             if self._shadow_ptrs(p)[0]:
                 p._rocket_shadow_live = True
@@ -204,11 +274,27 @@ class _FusedBase(torch.optim.Optimizer):
         lib = _lib.kernels()
         dev = self._device
         amp = self.amp if self.amp is not None else self._torch_amp if self._torch_amp is not None else self.guard
+        clip = None
+        if self.max_grad_norm is not None:
+            # the global norm needs every final gradient before any element is updated: a launch of
+            # its own, whose last block leaves the coefficient where the update reads it
+            clip = self._clip
+            if clip is None or self._partials is None or self._partials.numel() < self._nblocks:
+                raise RuntimeError(f"{type(self).__name__}: prepare() must run after set_grad_clip()")
+            _lib.check(
+                lib.rk_grad_norm_mt(self._gdtype, self._tables[0].data_ptr(), self._tables[1].data_ptr(),
+                                    self._nblocks, _lib.ptr(amp), self._partials.data_ptr(), clip.data_ptr(),
+                                    self._norm_ring.data_ptr(), self._norm_slot.data_ptr(), self._norm_ring.numel(),
+                                    self._norm_tickets.data_ptr(), self._chunk, _lib.stream_ptr(dev)),
+                "rk_grad_norm_mt",
+            )
+            if not torch.cuda.is_current_stream_capturing():
+                self.norm_launches += 1  # a replayed capture is counted by whoever replays it
         _lib.check(
             lib.rk_optim_mt(self.KIND, self._gdtype, self._tables[0].data_ptr(), self._tables[1].data_ptr(),
                             self._nblocks, self._hyper_dev.data_ptr(), self._step_dev.data_ptr(), _lib.ptr(amp),
-                            _lib.Workspace.get(dev).counter(f"optim_{id(self)}"), int(zero_grads), self._chunk,
-                            _lib.stream_ptr(dev)),
+                            _lib.ptr(clip), _lib.Workspace.get(dev).counter(f"optim_{id(self)}"), int(zero_grads),
+                            self._chunk, _lib.stream_ptr(dev)),
             "rk_optim_mt",
         )
 
@@ -367,7 +453,10 @@ class _FusedBase(torch.optim.Optimizer):
 
 
 class FusedAdamW(_FusedBase):
-    """AdamW with decoupled weight decay (``torch.optim.AdamW`` semantics, no amsgrad)."""
+    """AdamW with decoupled weight decay (``torch.optim.AdamW`` semantics, no amsgrad).
+
+    ``set_grad_clip(max_norm)`` clips the gradients to a global L2 norm inside the update (one extra
+    norm launch, no host read, graph-capturable); ``grad_norm`` is a device view of the last norm."""
 
     KIND = 0
     STATE_KEYS = ("exp_avg", "exp_avg_sq")
@@ -391,7 +480,10 @@ class FusedAdamW(_FusedBase):
 
 
 class FusedAdam(FusedAdamW):
-    """Adam with L2 weight decay (``torch.optim.Adam`` semantics)."""
+    """Adam with L2 weight decay (``torch.optim.Adam`` semantics).
+
+    ``set_grad_clip(max_norm)`` clips the gradients to a global L2 norm inside the update (one extra
+    norm launch, no host read, graph-capturable); ``grad_norm`` is a device view of the last norm."""
 
     DECOUPLED = False
 
@@ -400,7 +492,10 @@ class FusedAdam(FusedAdamW):
 
 
 class FusedSGD(_FusedBase):
-    """SGD with momentum / dampening / nesterov / weight decay (``torch.optim.SGD`` semantics)."""
+    """SGD with momentum / dampening / nesterov / weight decay (``torch.optim.SGD`` semantics).
+
+    ``set_grad_clip(max_norm)`` clips the gradients to a global L2 norm inside the update (one extra
+    norm launch, no host read, graph-capturable); ``grad_norm`` is a device view of the last norm."""
 
     KIND = 1
     STATE_KEYS = ("momentum_buffer",)

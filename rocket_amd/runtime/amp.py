@@ -15,6 +15,10 @@ two launches with no host synchronisation:
    step counter included — when the flag is set, and its last block applies the growth/backoff
    rule of ``torch._amp_update_scale_`` and clears the flag.
 
+With gradient clipping set on the optimizer (``set_grad_clip``) its launch puts the norm launch
+between the two: it reads the same ``1/scale`` slot, so the norm and the clip coefficient are those
+of the unscaled gradients (``unscale_`` before the step sets that slot to 1: same result).
+
 Whether a step was skipped is only needed by the LR scheduler wrapper (accelerate does not step
 the scheduler after a skipped optimizer step); the update's last block publishes it into a
 host-mapped ring (``(n << 1) | skipped`` at slot ``n % 64`` for update number ``n``), which the host

@@ -76,6 +76,10 @@ class EngineOptimizer:
         self._skipped = False
         self._skip_lazy = False  # fp16 fused scaler: the flag lives on the device until asked for
         self._lazy_handle = None  # (pinned copy, event) of that flag (FusedGradScaler.last_handle)
+        # global-norm clipping for optimizers without a clip of their own (the Optimizer capsule's
+        # max_grad_norm; the fused optimizers clip inside their update instead: set_grad_clip)
+        self.clip_max_norm: Optional[float] = None
+        self.last_grad_norm = None  # what the last clip returned (a tensor; no host read here)
 
     @property
     def step_was_skipped(self) -> bool:
@@ -132,6 +136,9 @@ class EngineOptimizer:
     def step(self, closure: Callable | None = None):
         if not self.engine.sync_gradients:
             return None
+        if self.clip_max_norm is not None:
+            # (unscales first under a loss scaler; the scaler's step then skips its own unscale)
+            self.last_grad_norm = self.engine.clip_grad_norm_(self._params(), self.clip_max_norm)
         scaler = self.engine.scaler
         if isinstance(scaler, FusedGradScaler):
             out = scaler.step(self.optimizer, closure) if closure else scaler.step(self.optimizer)
@@ -168,7 +175,7 @@ class EngineOptimizer:
             if self.optimizer.prepare():
                 self.optimizer.launch(zero_grads=True)
             return
-        self.step()
+        self.step()  # (clips first when clip_max_norm is set)
         self.zero_grad(set_to_none)
 
     def __getattr__(self, name):
