@@ -148,6 +148,8 @@ class StepTrace:
                 if float(g[:, 3].min()) > 0:
                     wg[name]["median_old_loaded"] = us(g[:, 3].median())
                     wg[name]["median_loop_done"] = us(g[:, 4].median())
+                if float(g[:, 5].min()) > 0:  # LDS-staged tiles: the wave's DMA'd operands are in LDS
+                    wg[name]["median_operands_landed"] = us(g[:, 5].median())
         spans["wgrad_groups"] = wg
         g = self.gtr.cpu().double()
         g = g[g[:, 0] > 0]

@@ -19,6 +19,7 @@
 // Weight gradients accumulate in registers across the samples of a wave, are reduced across
 // the block's waves through LDS and added to the persistent f32 gradients with one atomic
 // per element per block.
+#include "handoff_layout.h"
 #include "rk_common.h"
 
 #include <cstdlib>
@@ -133,6 +134,10 @@ __device__ __forceinline__ int pos2(int w, int q) {
 //   forward  fragment (nt, ks)[lane] = W[16nt + lo][32ks + 8hi + j]     (B[k][n] = W[n][k])
 //   dgrad    fragment (it, ks)[lane] = W[32ks + 8hi + j][16it + lo]     (B[k][n] = W[k][n])
 constexpr int F0 = 400, F1 = 120, F2 = 84, F3 = 10;
+// features per record of the blocked hand-off tensors (handoff_layout.h): whole 128-byte lines
+constexpr int F0P = rk_handoff::padded(F0), F1P = rk_handoff::padded(F1), F2P = rk_handoff::padded(F2),
+              F3P = rk_handoff::padded(F3);
+static_assert(F0P == 400 && F1P == 128 && F2P == 96 && F3P == 16, "hand-off record sizes");
 constexpr int OFF_F1 = 0;                  // fc1 fwd: 8 n-tiles x 13 k-steps
 constexpr int OFF_F2 = OFF_F1 + 8 * 13;    // fc2 fwd: 6 x 4
 constexpr int OFF_F3 = OFF_F2 + 6 * 4;     // fc3 fwd: 1 x 3
@@ -284,7 +289,7 @@ static_assert(offsetof(FwdSmem, a1cl) % 16 == 0 && offsetof(FwdSmem, a2) % 16 ==
 struct ClsFwd {  // classifier operands of the fused forward
   const bf16x8* frag;
   const float *fb1, *fb2, *fb3;
-  uint16_t *a2T, *h1T, *h2T;  // transposed activations [features][N] for the weight gradients
+  uint16_t *a2T, *h1T, *h2T;  // activations for the weight gradients, blocked [N / 4][Fp][4] (handoff_layout.h)
   float* logits;              // [N][10]
   uint64_t* trace;            // optional phase timeline [blocks][kTraceStride]
 };
@@ -670,11 +675,11 @@ __device__ __forceinline__ void fwd_body(FwdSmem& sm, const float* __restrict__ 
           v[i] = col < F1 ? fmaxf(acc[i] + bb, 0.f) : 0.f;
           sm.k.h1[i][col] = c16(v[i]);
         }
-        if (col < F1) *(uint2*)(cf.h1T + (int64_t)col * N + n0) = pack4(v[0], v[1], v[2], v[3]);
+        *(uint2*)(cf.h1T + rk_handoff::offset(F1P, blockIdx.x, col)) = pack4(v[0], v[1], v[2], v[3]);  // pads: zeros
       }
-    } else {  // meanwhile: a2^T for the fc1 weight gradient
+    } else {  // meanwhile: the block's a2 record for the fc1 weight gradient
       for (int f = threadIdx.x - 512; f < F0; f += 512)
-        *(uint2*)(cf.a2T + (int64_t)f * N + n0) = make_uint2(
+        *(uint2*)(cf.a2T + rk_handoff::offset(F0P, blockIdx.x, f)) = make_uint2(
             (uint32_t)sm.a2[0][f] | ((uint32_t)sm.a2[1][f] << 16), (uint32_t)sm.a2[2][f] | ((uint32_t)sm.a2[3][f] << 16));
       if (threadIdx.x - 512 < SPB * 8) sm.k.h1[(threadIdx.x - 512) >> 3][128 + ((threadIdx.x - 512) & 7)] = 0;
     }
@@ -691,7 +696,7 @@ __device__ __forceinline__ void fwd_body(FwdSmem& sm, const float* __restrict__ 
           v[i] = col < F2 ? fmaxf(acc[i] + bb, 0.f) : 0.f;
           sm.k.h2[i][col] = c16(v[i]);
         }
-        if (col < F2) *(uint2*)(cf.h2T + (int64_t)col * N + n0) = pack4(v[0], v[1], v[2], v[3]);
+        *(uint2*)(cf.h2T + rk_handoff::offset(F2P, blockIdx.x, col)) = pack4(v[0], v[1], v[2], v[3]);  // pads: zeros
       }
     }
     // the backward's classifier fragments, issued once fc2 no longer waits on its own operands
@@ -800,7 +805,7 @@ struct ClsBwd {
   const bf16x8* frag;
   const float* dy;                  // dlogits [N][10] (already scaled by the upstream gradient)
   const uint16_t *h1T, *h2T;        // forward activations (ReLU masks)
-  uint16_t *dyT, *d2T, *d1T;        // transposed gradients for the weight-gradient launch
+  uint16_t *dyT, *d2T, *d1T;        // gradients for the weight-gradient launch, blocked like the activations
   // fused softmax cross-entropy (ce != 0): d(logits) is derived here from the saved logits and
   // the targets instead of being read from `dy`; the mean loss is reduced across blocks
   // (last-block ticket) and folded into the Loss capsule's device accumulator / report ring.
@@ -886,7 +891,7 @@ __device__ __forceinline__ void bwd_body(BwdSmem& sm, const float* __restrict__ 
         if (hi == 0)
           mk2 = make_uint2((uint32_t)sm.k.h2[0][col] | ((uint32_t)sm.k.h2[1][col] << 16),
                            (uint32_t)sm.k.h2[2][col] | ((uint32_t)sm.k.h2[3][col] << 16));
-      } else if (hi == 0) mk2 = *(const uint2*)(cb.h2T + (int64_t)(col < F2 ? col : 0) * N + nb);
+      } else if (hi == 0) mk2 = *(const uint2*)(cb.h2T + rk_handoff::offset(F2P, nb / SPB, col));
     }
     if (wave < 8) {
       const int col = 16 * wave + lo;
@@ -894,7 +899,7 @@ __device__ __forceinline__ void bwd_body(BwdSmem& sm, const float* __restrict__ 
         if (hi == 0)
           mk1 = make_uint2((uint32_t)sm.k.h1[0][col] | ((uint32_t)sm.k.h1[1][col] << 16),
                            (uint32_t)sm.k.h1[2][col] | ((uint32_t)sm.k.h1[3][col] << 16));
-      } else if (hi == 0) mk1 = *(const uint2*)(cb.h1T + (int64_t)(col < F1 ? col : 0) * N + nb);
+      } else if (hi == 0) mk1 = *(const uint2*)(cb.h1T + rk_handoff::offset(F1P, nb / SPB, col));
     }
   }
 
@@ -1017,7 +1022,7 @@ __device__ __forceinline__ void bwd_body(BwdSmem& sm, const float* __restrict__ 
         }
         lds_barrier();
         RK_TR(cb.trace, 3);
-        if (threadIdx.x < SPB * DYP || (threadIdx.x >= 256 && threadIdx.x < 256 + F3)) {
+        if (threadIdx.x < SPB * DYP || (threadIdx.x >= 256 && threadIdx.x < 256 + F3P)) {
           // pre-normalised by the batch size (keeps the gradients' magnitudes, and so their bf16
           // rounding, those of the mean); the weight-gradient launch applies N / (valid count)
           const float sc = cb.grad_scale / (float)N * (cb.gscale_dev ? *cb.gscale_dev : 1.f);
@@ -1025,9 +1030,9 @@ __device__ __forceinline__ void bwd_body(BwdSmem& sm, const float* __restrict__ 
             const int sl = threadIdx.x / DYP, o = threadIdx.x % DYP;
             sm.dyl[sl][o] = c16(o < F3 ? sc * sm.dyf[sl][o] : 0.f);
           } else {
-            const int o = threadIdx.x - 256;
-            *(uint2*)(cb.dyT + (int64_t)o * N + nbase) =
-                pack4(sc * sm.dyf[0][o], sc * sm.dyf[1][o], sc * sm.dyf[2][o], sc * sm.dyf[3][o]);
+            const int o = threadIdx.x - 256, oc = o < F3 ? o : 0;  // the record's whole line: pads are zeros
+            const uint2 v = pack4(sc * sm.dyf[0][oc], sc * sm.dyf[1][oc], sc * sm.dyf[2][oc], sc * sm.dyf[3][oc]);
+            *(uint2*)(cb.dyT + rk_handoff::offset(F3P, nbase / SPB, o)) = o < F3 ? v : make_uint2(0u, 0u);
           }
         }
         lds_barrier();
@@ -1035,10 +1040,11 @@ __device__ __forceinline__ void bwd_body(BwdSmem& sm, const float* __restrict__ 
         if (threadIdx.x < SPB * DYP) {
           const int sl = threadIdx.x / DYP, o = threadIdx.x % DYP;
           sm.dyl[sl][o] = c16(o < F3 ? cb.dy[(int64_t)(nbase + sl) * F3 + o] : 0.f);
-        } else if (threadIdx.x >= 256 && threadIdx.x < 256 + F3) {
+        } else if (threadIdx.x >= 256 && threadIdx.x < 256 + F3P) {
           const int o = threadIdx.x - 256;
-          const float* d = cb.dy + (int64_t)nbase * F3 + o;
-          *(uint2*)(cb.dyT + (int64_t)o * N + nbase) = pack4(d[0], d[F3], d[2 * F3], d[3 * F3]);
+          const float* d = cb.dy + (int64_t)nbase * F3 + (o < F3 ? o : 0);
+          const uint2 v = pack4(d[0], d[F3], d[2 * F3], d[3 * F3]);
+          *(uint2*)(cb.dyT + rk_handoff::offset(F3P, nbase / SPB, o)) = o < F3 ? v : make_uint2(0u, 0u);
         }
         lds_barrier();
       RK_TR(cb.trace, 4);
@@ -1056,7 +1062,7 @@ __device__ __forceinline__ void bwd_body(BwdSmem& sm, const float* __restrict__ 
             v[i] = (col < F2 && mk[i] > 0.f) ? acc[i] : 0.f;
             sm.d2l[i][col] = c16(v[i]);
           }
-          if (col < F2) *(uint2*)(cb.d2T + (int64_t)col * N + nbase) = pack4(v[0], v[1], v[2], v[3]);
+          *(uint2*)(cb.d2T + rk_handoff::offset(F2P, nbase / SPB, col)) = pack4(v[0], v[1], v[2], v[3]);  // pads: zeros
         }
       }
       lds_barrier();
@@ -1073,7 +1079,7 @@ __device__ __forceinline__ void bwd_body(BwdSmem& sm, const float* __restrict__ 
             v[i] = (col < F1 && mk[i] > 0.f) ? acc[i] : 0.f;
             sm.d1l[i][col] = c16(v[i]);
           }
-          if (col < F1) *(uint2*)(cb.d1T + (int64_t)col * N + nbase) = pack4(v[0], v[1], v[2], v[3]);
+          *(uint2*)(cb.d1T + rk_handoff::offset(F1P, nbase / SPB, col)) = pack4(v[0], v[1], v[2], v[3]);  // pads: zeros
         }
       }
       lds_barrier();
@@ -1503,7 +1509,8 @@ RK_API int rk_lenet_frag_bytes() { return NFRAG * 64 * 16; }
 #endif
 
 // Whole LeNet forward (conv stack + classifier) for N % 8 == 0: logits [N][10] fp32, plus the
-// saved state of the fused backward (a1, codes) and the transposed activations of the wgrads.
+// saved state of the fused backward (a1, codes) and the activations of the wgrads (a2T / h1T / h2T:
+// blocked [N / 4][400 / 128 / 96][4], handoff_layout.h).
 // Diagnostics: phase timelines of the fused launches ([blocks][48] u64 each, or null = off).
 // (one pair of pointers, shared by the bf16 and fp16 builds of this file)
 #if RK_LENET_H
@@ -1543,7 +1550,8 @@ RK_API int RKL_NAME(rk_lenet_conv_bwd)(const float* x, const void* a1, const voi
 }
 
 // Fused backward for N % 8 == 0 (one block per 4 samples): classifier input-gradient chain from
-// dlogits, then the conv stack; writes dy^T, d2^T, d1^T and the conv-gradient slab for
+// dlogits, then the conv stack; writes dy, d2, d1 (blocked [N / 4][16 / 96 / 128][4], masks read from
+// the blocked h1T / h2T) and the conv-gradient slab for
 // rk_mlp3_wgrad, which accumulates all ten weight/bias gradients.
 struct LenetCE {  // host-side description of the fused cross-entropy (see ClsBwd)
   const float* logits;
@@ -1616,8 +1624,8 @@ RK_API int RKL_NAME(rk_lenet_bwd)(const float* x, const void* a1, const void* co
 }
 
 // Whole fused LeNet training step of the batch but the weight gradients, in ONE launch
-// (lenet_train_kernel): the rk_lenet_fwd outputs (logits, a1, codes, transposed activations) and
-// the rk_lenet_bwd outputs (transposed gradients, conv-gradient slab, loss partials) for a
+// (lenet_train_kernel): the rk_lenet_fwd outputs (logits, a1, codes, blocked activations) and
+// the rk_lenet_bwd outputs (blocked gradients, conv-gradient slab, loss partials) for a
 // softmax cross-entropy on `ce` (required; its d(logits) scale is ce->grad_scale).  rows (may be
 // null): the batch is gathered by this launch (RowSrc): x / ce->target are the batch buffers it fills.
 RK_API int RKL_NAME(rk_lenet_train)(const float* x, const float* b1, const float* b2, const void* frag, const float* fb1,

@@ -14,9 +14,12 @@
 //  mlp3_wgrad  All three dW_l += d_l^T-rows . x_l^T-rows (reduction over the batch) and the bias
 //              gradients (row sums of d_l^T) in ONE grouped launch: a block owns a 32x32 tile
 //              of one layer's dW, its 8 waves split the batch, partial tiles are reduced in LDS
-//              and added once — deterministic, no atomics.
+//              and added once — deterministic, no atomics.  For the fused LeNet step (lenet_conv.hip)
+//              the operands arrive in the blocked hand-off layout [M / 4][features][4]
+//              (handoff_layout.h) instead of [features][batch].
 //
 // Everything is branch-free in the load paths (clamped addresses + selects).
+#include "handoff_layout.h"
 #include "optim_common.h"
 #include "rows_common.h"
 
@@ -259,11 +262,12 @@ __global__ void __launch_bounds__(NT) mlp3_dgrad_kernel(const float* __restrict_
 
 // ------------------------------------------------------------------ grouped weight gradient
 struct WgradProb {
-  const uint16_t* dT;  // [N][M]
-  const uint16_t* xT;  // [K][M]
+  const uint16_t* dT;  // [N][M], or blocked [M / 4][Np][4] (handoff_layout.h)
+  const uint16_t* xT;  // [K][M], or blocked [M / 4][Kp][4]
   float* dw;           // [N][K], accumulated
   float* db;           // [N], accumulated (may be null)
   int N, K, tiles_k, tile_begin;
+  int Np, Kp;  // blocked layout: features per record
 };
 // optional column reduction riding on the same launch: dst[c] += sum_r slab[r][c] over the
 // [rows][width] slab of per-block partials (the fused LeNet backward's conv gradients); columns
@@ -289,7 +293,7 @@ struct LossFin {
 };
 struct WgradArgs {
   int late_ticket;  // LDS-staged dW tile blocks take the optimizer-step ticket after their operand wait
-  uint64_t* trace;  // optional phase stamps [blocks][8] (s_memrealtime): start, reduced, end, tile: old values in, main loop done
+  uint64_t* trace;  // optional phase stamps [blocks][8] (s_memrealtime): start, reduced, end, tile: old values in, main loop done, LDS-staged operands landed
   float gscale;     // every produced gradient is scaled by this (the upstream gradient factor)
   // normalisation by a count the backward left unapplied (the fused LeNet cross-entropy's mean,
   // pre-scaled by 1 / M): gradients are also scaled by M / sum(cnt_parts[0..ncnt)), and the loss
@@ -449,6 +453,15 @@ __device__ __forceinline__ bf16x8 rowfrag(const uint16_t* T, int R, int M, int r
   const uint4 z = make_uint4(0, 0, 0, 0);
   return __builtin_bit_cast(bf16x8, ok ? v : z);
 }
+// the same fragment of a blocked [M / 4][Fp][4] tensor: its two 4-sample halves
+__device__ __forceinline__ bf16x8 rowfrag_blocked(const uint16_t* T, int R, int Fp, int M, int r, int m0) {
+  const bool ok = r < R && m0 < M;
+  const int rr = r < R ? r : 0, mm = ok ? m0 : 0;
+  const uint2 a = *(const uint2*)(T + rk_handoff::frag_offset(Fp, mm, 0, rr));
+  const uint2 b = *(const uint2*)(T + rk_handoff::frag_offset(Fp, mm, 1, rr));
+  const uint4 z = make_uint4(0, 0, 0, 0);
+  return __builtin_bit_cast(bf16x8, ok ? make_uint4(a.x, a.y, b.x, b.y) : z);
+}
 
 
 // dW tile: WTN output features (rows of d^T) x 32 input features (rows of x^T).  16, not 32: the
@@ -457,14 +470,15 @@ __device__ __forceinline__ bf16x8 rowfrag(const uint16_t* T, int R, int M, int r
 constexpr int WTN = 16, WNI = WTN / 16, WEPT = WTN * 32 / NT;
 static_assert(WEPT >= 1 && WTN * 32 % NT == 0, "tile elements per thread");
 
-template <bool LDSV>
+// BLK: the operands are in the blocked hand-off layout of the fused LeNet step (handoff_layout.h)
+template <bool LDSV, bool BLK>
 __device__ void wgrad_tile(const WgradArgs& a, float (*red)[32 * 32], float (*rsum)[32], const rk_opt::AdamStep* ks,
                            const StepFill& sf, char* stage, unsigned* ticket);
 
 // LDSV: the tiles' operands arrive by LDS-DMA in whole 256-B row segments (16 KiB per wave: its 32 rows
 // of d^T and x^T over its 128 batch elements) and the MFMA fragments are read back from LDS, instead of
 // fragment-shaped global loads (16 rows x 64 B per instruction: half cache lines).  M % 512 == 0.
-template <bool LDSV>
+template <bool LDSV, bool BLK>
 __global__ void __launch_bounds__(NT) mlp3_wgrad_kernel(WgradArgs a) {
   if (a.trace && threadIdx.x == 0) a.trace[blockIdx.x * 8] = __builtin_amdgcn_s_memrealtime();
   __shared__ __attribute__((aligned(1024))) char stage[LDSV ? NW * 16384 : NW * 32 * 32 * 4];
@@ -503,7 +517,7 @@ __global__ void __launch_bounds__(NT) mlp3_wgrad_kernel(WgradArgs a) {
     if ((int)blockIdx.x - a.tiles < a.nslab) slab_reduce_block(a, blockIdx.x - a.tiles, red, ks, sf);
     else loss_fin_block(a.lf, red, sf);
   } else {
-    wgrad_tile<LDSV>(a, red, rsum, ks, sf, stage, late_ticket ? &ticket : nullptr);
+    wgrad_tile<LDSV, BLK>(a, red, rsum, ks, sf, stage, late_ticket ? &ticket : nullptr);
   }
   if (a.epi.on && threadIdx.x == 0 && ticket == gridDim.x - 1) {
     a.epi.step[0] = cur + 1.f;
@@ -512,7 +526,7 @@ __global__ void __launch_bounds__(NT) mlp3_wgrad_kernel(WgradArgs a) {
   if (a.trace && threadIdx.x == 0) a.trace[blockIdx.x * 8 + 2] = __builtin_amdgcn_s_memrealtime();
 }
 
-template <bool LDSV>
+template <bool LDSV, bool BLK>
 __device__ void wgrad_tile(const WgradArgs& a, float (*red)[32 * 32], float (*rsum)[32], const rk_opt::AdamStep* ks,
                            const StepFill& sf, char* stage, unsigned* ticket) {
   int pi = 0;
@@ -552,21 +566,37 @@ __device__ void wgrad_tile(const WgradArgs& a, float (*red)[32 * 32], float (*rs
 #if defined(__HIP_DEVICE_COMPILE__)
     // wave region: [WTN d rows][256 B] then [32 x rows][256 B]; row r's 16-B chunk c at c ^ (r & 15)
     // (the 16 rows a ds_read_b128 lane group reads hit 16 different bank slots); the LDS-DMA image
-    // is lane-linear, so the swizzle is applied to each lane's SOURCE chunk
+    // is lane-linear, so the swizzle is applied to each lane's SOURCE chunk.
+    // BLK: [32 records][16 d features x 8 B] then [32 records][32 x features x 8 B], a fragment is two
+    // ds_read_b64 (its 4-sample halves lie in neighbouring records); swizzle and addresses in
+    // handoff_layout.h.  Either way lane (lo, hi) at k-step s holds samples 32 s + 8 hi .. + 7 of feature
+    // lo in the same element order, so both layouts give bitwise the same gradients.
     char* const wst = stage + wv * 16384;
     constexpr int QD = WTN / 4;  // 1-KiB pieces of d rows
+    static_assert(!BLK || (WTN == rk_handoff::kDTile && QD == rk_handoff::kDPieces), "blocked layout: 16 x 32 tiles");
 #pragma unroll
     for (int q = 0; q < QD + 8; ++q) {  // 1 KiB each: 4 rows x 256 B
-      const int r = 4 * (q < QD ? q : q - QD) + (lane >> 4), c = lane & 15;
-      const uint16_t* T = q < QD ? P.dT : P.xT;
-      const int R = q < QD ? P.N : P.K, r0 = q < QD ? n0 : k0;
-      const int gr = min(r0 + r, R - 1);  // rows past the edge: any valid row (their outputs are not stored)
-      const uint16_t* src = T + (int64_t)gr * a.M + mb + 8 * (c ^ (r & 15));
+      const uint16_t* src;
+      if constexpr (BLK) {
+        // blocked: 8 (d) or 4 (x) records' whole 128- / 256-byte segments of the tile's features;
+        // the bank swizzle picks each lane's source chunk (handoff_layout.h)
+        namespace ho = rk_handoff;
+        if (q < QD) src = P.dT + ho::offset(P.Np, mb / 4 + ho::dma_d_rec(q, lane), n0 + ho::dma_d_feat(lane));
+        else src = P.xT + ho::offset(P.Kp, mb / 4 + ho::dma_x_rec(q - QD, lane),
+                                     ho::clamp_feat(k0 + ho::dma_x_feat(q - QD, lane), P.Kp));
+      } else {
+        const int r = 4 * (q < QD ? q : q - QD) + (lane >> 4), c = lane & 15;
+        const uint16_t* T = q < QD ? P.dT : P.xT;
+        const int R = q < QD ? P.N : P.K, r0 = q < QD ? n0 : k0;
+        const int gr = min(r0 + r, R - 1);  // rows past the edge: any valid row (their outputs are not stored)
+        src = T + (int64_t)gr * a.M + mb + 8 * (c ^ (r & 15));
+      }
       __builtin_amdgcn_global_load_lds((const void*)src,
                                        (__attribute__((address_space(3))) void*)(wst + q * 1024), 16, 0, 0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" ::: "memory");
+    if (a.trace && threadIdx.x == 0) a.trace[blockIdx.x * 8 + 5] = __builtin_amdgcn_s_memrealtime();  // operands landed
     // the optimizer step's ticket (see the kernel): its round trip overlaps the MFMAs and the
     // reduction; the value is needed only at the block's end
     if (ticket && a.epi.on && threadIdx.x == 0)
@@ -577,6 +607,17 @@ __device__ void wgrad_tile(const WgradArgs& a, float (*red)[32 * 32], float (*rs
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int ra = 16 * i + lo;
+        if constexpr (BLK) {  // two 8-byte reads: the fragment's halves lie in neighbouring records
+          namespace ho = rk_handoff;
+          if (i < WNI) {
+            const uint2 u = *(const uint2*)(wst + ho::lds_d(s4, hi, 0, ra)), v = *(const uint2*)(wst + ho::lds_d(s4, hi, 1, ra));
+            af[i] = __builtin_bit_cast(bf16x8, make_uint4(u.x, u.y, v.x, v.y));
+          }
+          const uint2 u = *(const uint2*)(wst + ho::kDBytes + ho::lds_x(s4, hi, 0, ra));
+          const uint2 v = *(const uint2*)(wst + ho::kDBytes + ho::lds_x(s4, hi, 1, ra));
+          bf[i] = __builtin_bit_cast(bf16x8, make_uint4(u.x, u.y, v.x, v.y));
+          continue;
+        }
         if (i < WNI) af[i] = *(const bf16x8*)(wst + ra * 256 + (((4 * s4 + hi) ^ (ra & 15)) * 16));
         bf[i] = *(const bf16x8*)(wst + WTN * 256 + ra * 256 + (((4 * s4 + hi) ^ (ra & 15)) * 16));
       }
@@ -603,6 +644,11 @@ __device__ void wgrad_tile(const WgradArgs& a, float (*red)[32 * 32], float (*rs
       const int mm = mk < me ? mk : a.M;  // a.M -> zero fragment
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
+        if constexpr (BLK) {
+          if (i < WNI) af[s][i] = rowfrag_blocked(P.dT, P.N, P.Np, a.M, n0 + 16 * i + lo, mm);
+          bf[s][i] = rowfrag_blocked(P.xT, P.K, P.Kp, a.M, k0 + 16 * i + lo, mm);
+          continue;
+        }
         if (i < WNI) af[s][i] = rowfrag(P.dT, P.N, a.M, n0 + 16 * i + lo, mm);
         bf[s][i] = rowfrag(P.xT, P.K, a.M, k0 + 16 * i + lo, mm);
       }
@@ -750,10 +796,12 @@ struct WgradEpi {
 // norm_by_count: the backward scaled by 1 / M instead of the loss's 1 / (valid count) and stored
 // per-block valid counts after its loss partials (loss->partials[nparts ..]): gradients are scaled
 // by M / their sum, the loss divided by it.
+// blocked: 0 = dT / xT are [features][M] (the stand-alone MLP head); 1 = the fused LeNet step's blocked
+// hand-off layout [M / 4][features padded to 16][4] (handoff_layout.h).
 RK_API int RKL_NAME(rk_mlp3_wgrad_loss)(int nprob, const void* const* dT, const void* const* xT, float* const* dw,
                               float* const* db, const int* Ns, const int* Ks, int M, const float* slab, int slab_rows,
                               int slab_width, float* const* slab_dst, const int* slab_bound, const LossFin* loss,
-                              const WgradEpi* epi, float gscale, int norm_by_count, hipStream_t s) {
+                              const WgradEpi* epi, float gscale, int norm_by_count, int blocked, hipStream_t s) {
   // the staged rows request (rk_mlp3_set_rows) belongs to THIS call whatever happens: taken and
   // cleared first, so an argument error below cannot leave it attached to a later launch
   const RowsReq rows_req = g_rows;
@@ -783,6 +831,8 @@ RK_API int RKL_NAME(rk_mlp3_wgrad_loss)(int nprob, const void* const* dT, const 
     a.p[i].db = db[j];
     a.p[i].N = Ns[j];
     a.p[i].K = Ks[j];
+    a.p[i].Np = rk_handoff::padded(Ns[j]);
+    a.p[i].Kp = rk_handoff::padded(Ks[j]);
     a.p[i].tiles_k = (Ks[j] + 31) / 32;
     a.p[i].tile_begin = tiles;
     if (i < nprob) tiles += ((Ns[j] + WTN - 1) / WTN) * a.p[i].tiles_k;
@@ -841,8 +891,14 @@ RK_API int RKL_NAME(rk_mlp3_wgrad_loss)(int nprob, const void* const* dT, const 
   // LDS-staged tile operands (mlp3_wgrad_kernel<true>) when every wave's batch range is 128 rows;
   // ROCKET_WGRAD_LDS=0 keeps the fragment-shaped global loads
   static const int lds_env = getenv("ROCKET_WGRAD_LDS") ? atoi(getenv("ROCKET_WGRAD_LDS")) : 1;
-  if (lds_env && M == NW * 128) mlp3_wgrad_kernel<true><<<tiles + extra, NT, 0, s>>>(a);
-  else mlp3_wgrad_kernel<false><<<tiles + extra, NT, 0, s>>>(a);
+  const bool lds = lds_env && M == NW * 128;
+  if (blocked) {
+    if (lds) mlp3_wgrad_kernel<true, true><<<tiles + extra, NT, 0, s>>>(a);
+    else mlp3_wgrad_kernel<false, true><<<tiles + extra, NT, 0, s>>>(a);
+  } else {
+    if (lds) mlp3_wgrad_kernel<true, false><<<tiles + extra, NT, 0, s>>>(a);
+    else mlp3_wgrad_kernel<false, false><<<tiles + extra, NT, 0, s>>>(a);
+  }
   return (int)hipGetLastError();
 }
 
@@ -850,5 +906,5 @@ RK_API int RKL_NAME(rk_mlp3_wgrad)(int nprob, const void* const* dT, const void*
                          const int* Ns, const int* Ks, int M, const float* slab, int slab_rows, int slab_width,
                          float* const* slab_dst, const int* slab_bound, hipStream_t s) {
   return RKL_NAME(rk_mlp3_wgrad_loss)(nprob, dT, xT, dw, db, Ns, Ks, M, slab, slab_rows, slab_width, slab_dst, slab_bound,
-                            nullptr, nullptr, 1.f, 0, s);
+                            nullptr, nullptr, 1.f, 0, 0, s);
 }

@@ -403,16 +403,17 @@ class _LeNetFused(torch.autograd.Function):
         a1 = torch.empty(N, 1176, **bf)
         c1 = torch.empty(N, 1176, dtype=torch.uint8, device=dev)
         c2 = torch.empty(N, 400, dtype=torch.uint8, device=dev)
-        a2T = torch.empty(400, N, **bf)
-        h1T = torch.empty(120, N, **bf)
-        h2T = torch.empty(84, N, **bf)
+        # hand-off tensors of the weight-gradient launch: blocked [N / 4][features padded to 16][4]
+        a2T = torch.empty(N // 4, 400, 4, **bf)
+        h1T = torch.empty(N // 4, 128, 4, **bf)
+        h2T = torch.empty(N // 4, 96, 4, **bf)
         logits = torch.empty(N, 10, dtype=torch.float32, device=dev)
         ctx.spec = None
         # (grad mode is off inside Function.forward: whether a backward can follow is needs_input_grad)
         if (target is not None and frags.spec_ok and any(ctx.needs_input_grad[1:11]) and N <= 65536 and target.dim() == 1
                 and target.numel() == N and target.dtype == torch.int64 and target.is_contiguous()
                 and target.device == dev):
-            dyT, d2T, d1T = torch.empty(10, N, **bf), torch.empty(84, N, **bf), torch.empty(120, N, **bf)
+            dyT, d2T, d1T = (torch.empty(N // 4, fp, 4, **bf) for fp in (16, 96, 128))
             slab = torch.empty(N // 4, int(lib.rk_lenet_slab_width()), dtype=torch.float32, device=dev)
             partials = torch.empty(2 * (N // 4), dtype=torch.float32, device=dev)  # loss sums, valid counts
             loss_out = torch.empty(2, dtype=torch.float32, device=dev)
@@ -508,9 +509,7 @@ class _LeNetFused(torch.autograd.Function):
         else:
             dy = dlogits.contiguous().float()
         bf = dict(dtype=a1.dtype, device=dev)
-        dyT = torch.empty(10, N, **bf)
-        d2T = torch.empty(84, N, **bf)
-        d1T = torch.empty(120, N, **bf)
+        dyT, d2T, d1T = (torch.empty(N // 4, fp, 4, **bf) for fp in (16, 96, 128))
         # conv weight/bias gradients: one slab row per backward block, summed by the wgrad launch
         slab = torch.empty(N // 4, int(lib.rk_lenet_slab_width()), dtype=torch.float32, device=dev)
         _lib.check(_k(lib, "rk_lenet_bwd", ctx.frags.half)(x.data_ptr(), a1.data_ptr(), c1.data_ptr(), c2.data_ptr(), w2c.data_ptr(),
@@ -555,7 +554,7 @@ class _LeNetFused(torch.autograd.Function):
                                           (ctypes.c_void_p * 4)(*[bufs[i].data_ptr() for i in range(4)]), bounds,
                                           ctypes.byref(fin) if fin is not None else None,
                                           ctypes.byref(epi) if epi is not None else None, float(gscale),
-                                          int(fin is not None), stream),
+                                          int(fin is not None), 1, stream),
                    "rk_mlp3_wgrad_loss")
         if rows_staged:
             pend.mark_advanced()  # only once the launch that advances the cursor was accepted

@@ -64,6 +64,7 @@ other input is copied into a static buffer before replay.
 from __future__ import annotations
 
 import collections
+import gc
 import operator
 import os
 from typing import Any, Dict, List, Optional, Tuple
@@ -421,7 +422,15 @@ class StepGraphs:
                 from rocket_amd.runtime import comm as _comm
 
                 if not _comm.all_ranks_agree(err is None):
-                    logger.warning(f"overlapped capture failed on some rank ({err or 'peer failed'}); "
+                    why = str(err) if err is not None else "peer failed"
+                    # The caught error holds, through its traceback, the failed capture's graphs, and with
+                    # this frame it forms a cycle only the cyclic collector frees — at any later
+                    # allocation, also inside a later capture, where HIP refuses the graph's destruction
+                    # and its destructor aborts the process.  Dropped and collected here, where nothing
+                    # is capturing.
+                    err = None
+                    gc.collect()
+                    logger.warning(f"overlapped capture failed on some rank ({why}); "
                                    "every rank captures sync steps in split mode")
                     rep.force_split = True
                     torch.cuda.synchronize()

@@ -21,7 +21,7 @@ for N in (256, 1024, 64, 512):
     bf = dict(dtype=torch.bfloat16, device="cuda")
     outs = []
     for rep in range(40):
-        dyT, d2T, d1T = torch.empty(10, N, **bf), torch.empty(84, N, **bf), torch.empty(120, N, **bf)
+        dyT, d2T, d1T = (torch.empty(N // 4, fp, 4, **bf) for fp in (16, 96, 128))
         slab = torch.full((N // 4, W), float("nan"), device="cuda")
         _lib.check(lib.rk_lenet_bwd(xs.data_ptr(), a1.data_ptr(), c1.data_ptr(), c2.data_ptr(), w2c.data_ptr(),
                                     frag.data_ptr(), g.data_ptr(), h1T.data_ptr(), h2T.data_ptr(), dyT.data_ptr(),
